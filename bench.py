@@ -29,6 +29,11 @@ size, steps and warm-up, timed the same way in the same process right after the 
 record was measured on THIS kernel source (sha256 of csrc/conv_wino44.hip / conv_wino.hip / conv_bf16.hip), else null.  `cpu_baseline` times
 the CPU oracle (= the reference's computation, bit-exact) on this host's cores at BASELINE config 1 (rank 0, 1 GPU runs
 only).  `config` carries the step's FLOPs in the reference's formulation and as executed here.
+`--dump-outputs DIR` (after the timed steps, outside the timed region): what the LAST timed step computed, as float32 / float64 .npy files
+in DIR, one set per case (prefix `f32_` / `bf16_`): `loss` and `losses` (the step's returns: the total and one per loss function), `outputs` (every output group's
+frames, flattened in that order), `params` (the parameters after the Adam step) and `grads` (their gradients).  An array of more than 2^21 elements is
+written as a fixed sample of 2^21 of them (seeded, the same positions for the same shape), so a dump stays under 64 MB; the inputs and initial
+weights are seeded as well, so two builds run with the same arguments can be compared file by file.
 Diagnosis (environment, no effect on the numbers' definition): BENCH_EACH_STEP=1 prints every timed step's HIP-event time and host enqueue time to stderr;
 BENCH_DUMMY_STREAMS=<n> / BENCH_DUMMY_ALLOC_GB=<n> give a case the stream-pool position / allocator history an earlier case of the same process would have left
 (how the 5 % penalty of the second engine of a process was traced to its side streams, DESIGN.md 4d c).
@@ -107,6 +112,42 @@ def step_flops_bf16(T, U=6, S=3, L=3, scale=4):
     fwd = F * 1152 + 2 * nfr * L * lstm + nwin * (r1 + r2) + 3 * S * T * out_f
     bwd = T * 1152 + S * 2 * T * L * 2 * lstm + S * T * 2 * (r1 + r2) + 3 * S * T * out_b
     return fwd + bwd
+
+
+DUMP_MAX_ELEMENTS = 1 << 21           # per array of --dump-outputs: larger arrays are sampled
+DUMP_MAX_BYTES = 64 << 20             # all arrays of one run together
+DUMP_SEED = 20240601
+
+
+def dump_array(dump_dir, name, t, written):
+    """Write tensor `t` (flattened) as dump_dir/name.npy: float64 stays float64, everything else becomes float32; more than DUMP_MAX_ELEMENTS
+    elements are reduced to a seeded sample of that many (sorted positions, the same for the same length).  `written` counts the bytes of the run."""
+    import numpy as np
+    t = t.detach().reshape(-1).cpu()
+    t = t.double() if t.dtype == torch.float64 else t.float()
+    if t.numel() > DUMP_MAX_ELEMENTS:
+        g = torch.Generator().manual_seed(DUMP_SEED)
+        t = t[torch.randint(t.numel(), (DUMP_MAX_ELEMENTS,), generator=g).sort().values]
+    a = t.numpy()
+    written[0] += a.nbytes
+    if written[0] > DUMP_MAX_BYTES:
+        raise SystemExit(f'bench.py: --dump-outputs would write more than {DUMP_MAX_BYTES >> 20} MB')
+    np.save(os.path.join(dump_dir, name + '.npy'), a)
+
+
+def dump_step(dump_dir, tag, result, net, written):
+    """The arrays a caller of the training step holds after it: its returns (outputs, loss, one loss per loss function) and the updated parameters
+    with their gradients."""
+    outputs, loss, losses = result
+    os.makedirs(dump_dir, exist_ok=True)
+    dump_array(dump_dir, f'{tag}_loss', loss.detach().double().reshape(1), written)
+    dump_array(dump_dir, f'{tag}_losses', torch.stack([v.detach().double().reshape(()) for v in losses]), written)
+    dump_array(dump_dir, f'{tag}_outputs', torch.cat([o.detach().reshape(-1).float().cpu() for stage in outputs if stage is not None
+                                                      for o in stage if o is not None]), written)
+    params = list(net.parameters())
+    dump_array(dump_dir, f'{tag}_params', torch.cat([p.detach().reshape(-1).float().cpu() for p in params]), written)
+    dump_array(dump_dir, f'{tag}_grads', torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float().cpu()
+                                                    for p in params]), written)
 
 
 def make_net(dev, seed=0, scale=4):
@@ -359,9 +400,13 @@ def run_case(args, dtype, dev, world, rank):
     t0 = time.perf_counter()
     marks[0].record()
     host = []
+    last = None
     for i in range(args.steps):
         h0 = time.perf_counter()
-        _, loss, _ = tr.train_step(inputs, targets, pos)
+        res = tr.train_step(inputs, targets, pos)
+        loss = res[1]
+        last = res if args.dump_outputs and i == args.steps - 1 else None
+        del res
         marks[i + 1].record()
         host.append(time.perf_counter() - h0)
     barrier()
@@ -399,6 +444,10 @@ def run_case(args, dtype, dev, world, rank):
     peak = PEAK_BF16_MFMA_TFLOPS if bf else PEAK_F32_MFMA_TFLOPS
     prec = ('bf16 storage + bf16 MFMA, fp32 accumulate (BASELINE config 3 per GPU)' if bf else 'fp32')
     out = None
+    if last is not None:
+        if rank == 0:
+            dump_step(args.dump_outputs, dtype, last, net, args.dump_written)
+        del last
     if rank == 0:
         roof = lstm_kernel_roofline(net, dev, args.batch, args.size, args.size)
         out = {
@@ -461,11 +510,17 @@ def parse_args(argv=None):
     ap.add_argument('--allow-overrides', action='store_true',
                     help='print the line although RNH_* A/B switches are set in the environment (hipvsr/forms.py: SWITCHES); they are listed in config.forms.env_overrides '
                          'either way.  Without this flag a run with overrides is refused: a stray variable on a box must not silently change the headline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed (outputs, losses, updated parameters, gradients) as .npy files '
+                         'to DIR, at most 64 MB in all (see the module docstring)')
     ap.add_argument('--dry-run', action='store_true',
                     help='no GPU: the launch / rendezvous / barrier / max-over-ranks protocol over gloo with a stub step (what tests/ checks on CPU)')
     ap.add_argument('--dry-run-fail-rank', type=int, default=-1, help=argparse.SUPPRESS)
     ap.add_argument('--dry-run-slow-rank', type=int, default=-1, help=argparse.SUPPRESS)
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    args.dump_written = [0]
     c = CONFIGS[args.config]
     args.scale = c['scale']
     for k in ('batch', 'frames', 'size'):

@@ -3,8 +3,8 @@
 The reference's predictor (src/runner/predictors/acdc_vsr_refinenet_predictor.py:31-109) runs ``net(inputs, pos_codes)``
 under ``torch.no_grad()`` on ONE whole cardiac cycle at a time (batch 1, F = T_cycle + 2U frames of e.g. 54 x 64 pixels):
 about a thousand sub-20-microsecond launches, i.e. bound by the host's launch rate, not by the GPU.  ``GraphedForward``
-captures the engine's forward once per input shape - the layer/frame wavefront of the ConvLSTM on its 2L side streams
-becomes parallel branches of the graph - and replays it with one ``hipGraphLaunch``.
+captures the engine's forward once per input shape - as one chain of launches in issue order: the engine's side streams are
+not used while it captures (``HipOps.linear_capture``) - and replays it with one ``hipGraphLaunch``.
 
 Static buffers: the inputs are copied into the graph's input buffer (one small D2D copy), the outputs are views of the
 graph's output buffer and are overwritten by the next call with the same shape; weights are read (and re-packed) inside
@@ -53,8 +53,13 @@ class GraphedForward:
             self.net(static_in, e.pos)             # eager run on the capture stream: plans, index maps, workspaces exist afterwards
         st.synchronize()
         e.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(e.graph, stream=st), torch.no_grad():
-            e.outputs = self.net(static_in, e.pos)
+        ops = self.net._engine().ops
+        ops.linear_capture = True                  # one chain of launches (HipOps.fork)
+        try:
+            with torch.cuda.graph(e.graph, stream=st), torch.no_grad():
+                e.outputs = self.net(static_in, e.pos)
+        finally:
+            ops.linear_capture = False
         e.replays = 0
         return e
 
@@ -94,8 +99,8 @@ class GraphedTrainStep:
     (configs/train/refine_net/exp1_x4.yaml:21-33: batch 16, 32 x 32 crops) the step is GPU-bound, not launch-bound - fp32 50.9 ms
     eager against 51.3 ms replayed, bf16 24.2 against 27.0 (slower) - so the trainer does NOT use this class unless asked to
     (trainer kwarg ``graph: true``); it is kept for smaller batches, where a step is ~1 500 launches of a few microseconds each.
-    The whole step up to the gradients is captured once per input shape - the ConvLSTM wavefront's side streams become parallel
-    branches - and replayed with one launch; what stays outside: the copy of the batch into the graph's static input buffers,
+    The whole step up to the gradients is captured once per input shape - one chain of launches, without the side streams
+    (``HipOps.linear_capture``) - and replayed with one launch; what stays outside: the copy of the batch into the graph's static input buffers,
     the gradient all-reduce (one collective; single rank only, the trainer refuses the combination), the optimizer step (two
     launches of the flat Adam whose step count and learning rate are host-side arguments) and metrics / logging.
 
@@ -151,8 +156,13 @@ class GraphedTrainStep:
         # default global mode would reject as 'operation not permitted when stream is capturing'
         import torch.distributed as dist
         mode = 'thread_local' if dist.is_available() and dist.is_initialized() else 'global'
-        with torch.cuda.graph(e.graph, stream=st, capture_error_mode=mode):
-            e.outputs, e.loss, e.losses = self._body(e)
+        ops = net._engine().ops
+        ops.linear_capture = True                  # one chain of launches (HipOps.fork)
+        try:
+            with torch.cuda.graph(e.graph, stream=st, capture_error_mode=mode):
+                e.outputs, e.loss, e.losses = self._body(e)
+        finally:
+            ops.linear_capture = False
         e.grads = [p.grad for p in params]
         e.flat = net._flat_grad
         e.replays = 0

@@ -320,8 +320,29 @@ def g7_metrics_adam(mods):
     print('g7_metrics.pt', {k: (float(v['trainer_psnr']), float(v['trainer_ssim'])) for k, v in cases.items() if isinstance(v, dict) and 'trainer_psnr' in v})
 
 
+def g8_reference_yamls():
+    """The reference's own RefineNet YAMLs (configs/{train,test}/refine_net/exp*_x*.yaml), parsed, as one JSON file: the
+    sections tests/test_main_config.py resolves against this package's classes."""
+    import json
+    import yaml
+    cfg_dir = os.path.join(os.path.dirname(REF.rstrip('/')), 'configs')
+    out = {}
+    for split in ('train', 'test'):
+        for i, s in ((1, 4), (2, 3), (3, 2)):
+            name = f'exp{i}_x{s}.yaml'
+            with open(os.path.join(cfg_dir, split, 'refine_net', name)) as f:
+                out[f'{split}/{name}'] = yaml.safe_load(f)
+    with open(os.path.join(HERE, 'g8_reference_yamls.json'), 'w') as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write('\n')
+    print('g8_reference_yamls.json', sorted(out))
+
+
 if __name__ == '__main__':
     torch.set_num_threads(8)
+    if sys.argv[1:] == ['g8']:
+        g8_reference_yamls()
+        sys.exit(0)
     mods = _load_reference()
     if sys.argv[1:] == ['g6']:
         g6_input()
@@ -335,3 +356,4 @@ if __name__ == '__main__':
     g2_cfg1(mods)
     g6_input()
     g7_metrics_adam(mods)
+    g8_reference_yamls()

@@ -138,3 +138,33 @@ def test_committed_pmc_records_belong_to_the_committed_kernel_sources():
         assert rec['kernel_source_sha256'] == bench.kernel_source_sha256(source), f'{record} was measured on another revision of {source}: re-run tools/prof_pmc_*.sh'
         traffic, src = bench.quoted_traffic(record, source, (8, 128, 128))
         assert traffic and traffic > rec['algorithmic_bytes_per_launch'] * 0.9 and src['command']
+
+
+def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path):
+    """--dump-outputs: the step's returns and the updated parameters / gradients as float32 / float64 .npy, an array larger than
+    bench.DUMP_MAX_ELEMENTS as a seeded sample of the same positions every time, all of it under 64 MB; --steps must be at least 1."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    net = torch.nn.Linear(3000, 1000)
+    net.weight.grad, net.bias.grad = torch.ones_like(net.weight), None
+    outs = [None, [torch.randn(2, 1, 1024, 600).to(torch.bfloat16) for _ in range(3)]]
+    res = (outs, torch.tensor(1.5), [torch.tensor(0.25, dtype=torch.float64)])
+    for d in ('a', 'b'):
+        bench.dump_step(str(tmp_path / d), 'f32', res, net, [0])
+    names = sorted(os.listdir(tmp_path / 'a'))
+    assert names == ['f32_grads.npy', 'f32_loss.npy', 'f32_losses.npy', 'f32_outputs.npy', 'f32_params.npy']
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / 'a' / n), np.load(tmp_path / 'b' / n)
+        assert a.dtype in (np.float32, np.float64) and a.size <= bench.DUMP_MAX_ELEMENTS and np.array_equal(a, b)
+        total += a.nbytes
+    assert total <= bench.DUMP_MAX_BYTES
+    assert float(np.load(tmp_path / 'a' / 'f32_loss.npy')[0]) == 1.5
+    full = torch.cat([o.reshape(-1).float() for o in outs[1]])
+    assert np.isin(np.load(tmp_path / 'a' / 'f32_outputs.npy'), full.numpy()).all()
+    with pytest.raises(SystemExit):
+        bench.dump_step(str(tmp_path / 'c'), 'f32', res, net, [bench.DUMP_MAX_BYTES])
+    r = _run(['--dry-run', '--steps', '0'])
+    assert r.returncode != 0 and '--steps' in r.stderr

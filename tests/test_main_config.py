@@ -59,24 +59,21 @@ def test_state_dict_roundtrip_with_reference_layout(golden_dir):
         assert torch.equal(v, c['state_dict'][k])
 
 
-REF_CFG = '/root/reference/configs'
 REF_YAMLS = [('train', f'exp{i}_x{s}.yaml') for i, s in ((1, 4), (2, 3), (3, 2))] + \
             [('test', f'exp{i}_x{s}.yaml') for i, s in ((1, 4), (2, 3), (3, 2))]
 
 
 @pytest.mark.parametrize('split,name', REF_YAMLS)
-def test_reference_refinenet_yamls_resolve_unchanged(split, name):
+def test_reference_refinenet_yamls_resolve_unchanged(split, name, golden_dir, tmp_path):
     """The boundary claim "src.main + configs/train/refine_net/exp1_x4.yaml run unchanged" (reference src/main.py:59,
     :170-181): every section of the reference's own RefineNet YAMLs (ACDC; its *_dsb15.yaml files name a dataset class the
-    reference does not contain) resolves by name against this package and constructs with the YAML's kwargs.  Reads
-    /root/reference, which only exists in the build container: skipped elsewhere."""
-    path = os.path.join(REF_CFG, split, 'refine_net', name)
-    if not os.path.exists(path):
-        pytest.skip('the reference tree is not present on this machine')
+    reference does not contain) resolves by name against this package and constructs with the YAML's kwargs.  The YAMLs are
+    read as parsed by tests/golden/make_golden.py (g8_reference_yamls.json)."""
+    import json
     import src
     from src.main import Cfg, _get_instance, _losses_metrics
-    with open(path) as f:
-        cfg = Cfg(yaml.safe_load(f))
+    with open(os.path.join(golden_dir, 'g8_reference_yamls.json')) as f:
+        cfg = Cfg(json.load(f)[f'{split}/{name}'])
     # net: constructed with the YAML's kwargs, parameter count of the reference (base_net.py:11-13)
     net = _get_instance(src.model.nets, cfg.net)
     from oracle import refinenet_oracle as orc
@@ -109,7 +106,7 @@ def test_reference_refinenet_yamls_resolve_unchanged(split, name):
     if split == 'train':
         assert cfg.optimizer.name == 'Adam' and hasattr(torch.optim, cfg.optimizer.name)
         assert hasattr(src.callbacks.loggers, cfg.logger.name)
-        mon = getattr(src.callbacks.monitor, cfg.monitor.name)(checkpoints_dir=os.path.join('/tmp', 'rnh_mon_test'), **cfg.monitor.kwargs)
+        mon = getattr(src.callbacks.monitor, cfg.monitor.name)(checkpoints_dir=str(tmp_path / 'checkpoints'), **cfg.monitor.kwargs)
         assert mon.early_stop == float('inf')                       # early_stop: 0 in the YAML = never
         tr = getattr(src.runner.trainers, cfg.trainer.name)
         import inspect
